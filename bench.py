@@ -173,6 +173,23 @@ def train_measure(args, steps, warmup, cpu=True, quiet=False):
     return line
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array as out_dir/<name>.npy in float32, at most DUMP_MAX_BYTES in all.  An array over its
+    share of that budget is replaced by a fixed, seeded sample of its flattened elements (same positions on every run)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_MAX_BYTES // max(len(arrays), 1)
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy().astype(np.float32, copy=False)
+        if a.nbytes > share:
+            idx = np.sort(np.random.RandomState(0).choice(a.size, share // 4, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def train_bench(args):
     print(json.dumps(train_measure(args, args.steps, args.warmup)))
 
@@ -232,6 +249,8 @@ def main():
     ap.add_argument("--small", action="store_true", help="reduced-depth experts (plumbing check only, not a valid bench)")
     ap.add_argument("--gemm", choices=["f32", "bf16x3", "bf16"], default=None,
                     help="GEMM arithmetic (default: the engine's default, bf16x3; bf16 = plain bf16 operands, a precision option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy (float32)")
     ap.add_argument("--dry-run", action="store_true",
                     help="launch / rendezvous / broadcast / timing plumbing only, no engine and no GPU (CPU tests; not a bench)")
     args = ap.parse_args()
@@ -247,6 +266,8 @@ def main():
 
         procs, threads, _ = S.launch_ranks(args.gpus, [sys.executable, os.path.abspath(__file__)] + sys.argv[1:], relay=relay)
         sys.exit(S.join_ranks(procs, threads))
+    if args.dump_outputs and (args.config == "train" or args.dry_run):
+        raise SystemExit("--dump-outputs writes the inference path's output: not with --config train or --dry-run")
     if args.config == "train":
         return train_bench(args)
     if args.dry_run:
@@ -311,6 +332,10 @@ def main():
         torch.distributed.all_reduce(tmax, op=torch.distributed.ReduceOp.MAX)
     dt = float(tmax.item())
     log(f"timed {args.steps} steps: {1e3 * dt / args.steps:.1f} ms/step")
+    if args.dump_outputs and rank == 0:
+        # the SR images of the last timed step, as a caller of process() receives them ([B, 3, 4h, 4w] in [0, 1])
+        dump_outputs(args.dump_outputs, {"sr": E.map_to_nchw(outs[-1])})
+        log(f"outputs of the last timed step written to {args.dump_outputs}")
 
     mp_per_image = (h * SCALE) * (w * SCALE) / 1e6
     value = world * args.steps * args.batch * mp_per_image / dt

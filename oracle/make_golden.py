@@ -370,8 +370,64 @@ def golden_flags():
                 "simple": simple, "variants": outs}, os.path.join(GOLDEN, "fusion_flags.pt"))
 
 
+def recheck_inputs():
+    """the inputs of tests/test_oracle_vs_reference.py: two seeded cached-feature batches and one metric pair"""
+    eval_case = train_case(123, 1, 24, 40)
+    grad_case = train_case(124, 2, 16, 16)
+    a = lr_input(55, 1, 40, 56)
+    b = (a + 0.04 * torch.randn(a.shape, generator=torch.Generator().manual_seed(5))).clamp(-0.1, 1.1)
+    return eval_case, grad_case, (a, b)
+
+
+RECHECK_GRAD_SAMPLE = 256
+
+
+def recheck_grad_index(numel):
+    """flat positions of a parameter's gradient kept in recheck.pt: all of a small parameter, a fixed seeded sample of
+    RECHECK_GRAD_SAMPLE positions of a larger one (numpy's legacy RandomState stream is stable across versions)"""
+    import numpy as np
+    if numel <= RECHECK_GRAD_SAMPLE:
+        return torch.arange(numel)
+    return torch.from_numpy(np.sort(np.random.RandomState(numel).choice(numel, RECHECK_GRAD_SAMPLE, replace=False)))
+
+
+def golden_recheck():
+    """the REFERENCE's outputs on recheck_inputs() -> tests/golden/recheck.pt (fp32): the eval forward of the fusion net
+    (weights of fusion_full.pt), the gradient of every parameter after L1(forward.clamp(0,1), hr) in train mode (dropout 0),
+    and calculate_psnr / calculate_ssim of the pair at (crop 0, RGB) and (crop 4, Y).  A gradient is stored as its exact
+    max|g|, the float64 sum and L2 norm of the whole tensor, and its values at recheck_grad_index(numel) (all of them for
+    small parameters), which keeps the fixture small."""
+    import torch.nn.functional as F
+    ref = load_reference()
+    sd = {k: (v.float() if v.is_floating_point() else v) for k, v in torch.load(os.path.join(GOLDEN, "fusion_full.pt"),
+                                                                                 weights_only=True)["sd"].items()}
+    (lr, imgs, feats, _), (lr2, imgs2, feats2, hr2), (a, b) = recheck_inputs()
+    m = ref.CompleteEnhancedFusionSR(expert_ensemble=None)
+    m.load_state_dict(sd, strict=False)
+    with torch.no_grad():
+        sr = m.eval().forward_with_precomputed(lr, imgs, feats)
+    m.load_state_dict(sd, strict=False)
+    m.train()
+    m.cross_band.band_attention.dropout = 0.0
+    m.collaborative.cross_attn.dropout = 0.0
+    F.l1_loss(m.forward_with_precomputed(lr2, imgs2, feats2).clamp(0, 1), hr2).backward()
+    names = [k for k, _ in m.named_parameters()]
+    grads = {"names": names,      # one flat tensor each: max|g| per parameter, the kept values in `names` order
+             "max": torch.stack([p.grad.abs().max() for _, p in m.named_parameters()]),
+             "values": torch.cat([p.grad.detach().reshape(-1)[recheck_grad_index(p.numel())] for _, p in m.named_parameters()]),
+             "sum": torch.stack([p.grad.double().sum() for _, p in m.named_parameters()]),
+             "l2": torch.stack([p.grad.double().norm() for _, p in m.named_parameters()])}
+    met = _load_reference_file("src/utils/metrics.py", "ref_src_utils_metrics_recheck")
+    metrics = {(crop, y): (float(met.calculate_psnr(a, b, crop_border=crop, test_y_channel=y)),
+                           float(met.calculate_ssim(a, b, crop_border=crop, test_y_channel=y)))
+               for crop, y in ((0, False), (4, True))}
+    torch.save({"sr": sr, "grads": grads, "metrics": metrics}, os.path.join(GOLDEN, "recheck.pt"))
+
+
 if __name__ == "__main__":
-    what = sys.argv[1:] or ["inference", "metrics", "train", "flags"]
+    what = sys.argv[1:] or ["inference", "metrics", "train", "flags", "recheck"]
+    if "recheck" in what:
+        golden_recheck()
     if "flags" in what:
         golden_flags()
     if "inference" in what:
