@@ -13,7 +13,6 @@ or several micro-batches (accumulation_steps, train.py:332) need nothing extra.
 """
 from __future__ import annotations
 
-import os
 from typing import List, Optional, Sequence
 
 import torch
@@ -23,7 +22,6 @@ from .ops import ACT_GELU, ACT_LRELU, ACT_NONE, ACT_RELU, ACT_SIGMOID, _mat, _pt
 
 ACT_CLAMP01, ACT_CLAMP_MIN = 6, 7        # codes of ffsr_act_bwd_f32 only
 N_PARTIAL = 1024
-WGRAD_BF16X3 = os.environ.get("FFSR_WGRAD_BF16X3", "1") != "0"   # =0: every weight gradient on the exact f32 MFMA kernels (A/B runs)
 
 
 class Var:
@@ -118,9 +116,9 @@ def conv_tile(M: int, N: int, taps: int, cin: int = 0) -> int:
     """explicit tile_hint of ops.conv2d for fp32-map inputs: the split-bf16 kernel where the default mode would take it,
     else the exact f32 kernel (also FFSR_GEMM_MODE=f32).  0 = ops.conv2d's own choice: for the wide k x k layers at HR (the refine
     stack, forward and input gradient) that is one split pass + the planes tap-strip kernel (2.2 vs 2.8 ms per layer at config 5)."""
-    if ops.GEMM_MODE == "bf16x3" and ops.PLANES_AUTO and taps > 1 and cin >= 32 and cin % 32 == 0 and N > 64 and M >= 16384:
+    if ops.split_mode() and taps > 1 and cin >= 32 and cin % 32 == 0 and N > 64 and M >= 16384:
         return 0
-    if ops.GEMM_MODE == "bf16x3" and M > 64 * 24 and taps <= 32:
+    if ops.split_mode() and M > 64 * 24 and taps <= 32:
         return 32 if N <= 32 else 64
     if N <= 32:
         return 13
@@ -263,7 +261,7 @@ class Tape:
             else:
                 gz = gy
             part = torch.empty(_wgrad_scratch(p), device=self.device)
-            hip.call("ffsr_conv_wgrad_bf16x3" if ops.GEMM_MODE == "bf16x3" and WGRAD_BF16X3 else "ffsr_conv_wgrad_f32", _ptr(xm), ops.ld(xm), _ptr(gz), ops.ld(gz), _ptr(p.weight.g),
+            hip.call("ffsr_conv_wgrad_bf16x3" if ops.split_mode() else "ffsr_conv_wgrad_f32", _ptr(xm), ops.ld(xm), _ptr(gz), ops.ld(gz), _ptr(p.weight.g),
                      None if p.bias is None else _ptr(p.bias.g), _ptr(part),
                      part.numel(), B, H, W, p.Cin, p.N, p.KH, p.KW, p.pad, p.pad, _stream())
             if x.req:
@@ -279,9 +277,9 @@ class Tape:
         3x3 layers (the planes tap-strip kernel's shapes) the activation between them lives as bf16 planes ONLY: the producing
         GEMM's epilogue writes the pre-activation z in fp32 (kept for GELU's backward) and GELU(z) as planes, which the next layer's
         forward GEMM and weight-gradient kernel both read -- no GELU pass, no split pass, no fp32 copy.  Other layers, other modes
-        (FFSR_GEMM_MODE=f32, FFSR_PLANES=0): plain Tape.conv."""
+        (FFSR_GEMM_MODE=f32): plain Tape.conv."""
         def planes_layer(p):
-            return (ops.GEMM_MODE == "bf16x3" and ops.PLANES_AUTO and WGRAD_BF16X3 and p.KH == 3 and p.KW == 3 and p.pad == 1
+            return (ops.split_mode() and p.KH == 3 and p.KW == 3 and p.pad == 1
                     and p.fwd.phi is not None and p.N % 128 == 0 and p.Cin % 128 == 0)
         B, H, W, _ = x.v.shape
         M = B * H * W

@@ -747,34 +747,16 @@ __global__ void dihedral_kernel(const float* __restrict__ in, int ldi, float* __
 
 inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
-// FFSR_DW_STRIP=0 keeps the run kernel everywhere (A/B measurements, tools/dw_bench.py)
-inline bool dw3x3_strip_enabled() {
-  static const int on = [] {
-    const char* e = getenv("FFSR_DW_STRIP");
-    return (e && e[0] == '0') ? 0 : 1;
-  }();
-  return on != 0;
-}
-
-inline int dw3x3_strip_maxc() {
-  static const int c = [] {
-    const char* e = getenv("FFSR_DW_STRIP_MAXC");
-    return e ? atoi(e) : 64;
-  }();
-  return c;
-}
+// dw3x3_gate_pool_f32 takes the strip kernel up to this many channels (wider maps keep the run kernel)
+constexpr int DW3X3_STRIP_MAXC = 64;
 
 // strip width of dw3x3_strip_kernel: the launch should have >= 8192 waves (measured: 1408 x 2048 x 64 gated 1504 / 830 / 506 /
 // 566 us with strips cut for 2048 / 4096 / 8192 / 16384 waves -- short strips keep more independent load streams in flight and
 // balance better than long ones save on their 2-column lead-in)
 inline int dw3x3_strip_width(int H, int W, int cgroups, int B) {
   const long long rows = (long long)((H + 3) / 4) * cgroups * B;
-  static const int target = [] {
-    const char* e = getenv("FFSR_DW_STRIP_WAVES");
-    return e ? atoi(e) : 8192;
-  }();
   int xs = 512;
-  while (xs > 32 && rows * ((W + xs - 1) / xs) < target) xs >>= 1;
+  while (xs > 32 && rows * ((W + xs - 1) / xs) < 8192) xs >>= 1;
   return xs;
 }
 
@@ -902,7 +884,7 @@ extern "C" int ffsr_dwconv2d_f32(const float* in, int ldi, const float* w, const
   if (KH == 3 && KW == 3 && pad_h == 1 && pad_w == 1 && pix >= 4096 && B <= 65535) {   // sliding-window kernel
     const long long per_img = (long long)H * W;
     const int nchunk = (int)(per_img / 256 < 1 ? 1 : (per_img / 256 > 8192 ? 8192 : per_img / 256));
-    if (dw3x3_strip_enabled() && pix >= 65536 && W >= 64 && pix * (ldi > ldo ? ldi : ldo) < (1ll << 31)) {     // measured: 163 vs 227 us at 352 x 512 x 360
+    if (pix >= 65536 && W >= 64 && pix * (ldi > ldo ? ldi : ldo) < (1ll << 31)) {     // measured: 163 vs 227 us at 352 x 512 x 360
       const int xs = dw3x3_strip_width(H, W, (C + 63) / 64, B);
       const int ns = ((H + 3) / 4) * ((W + xs - 1) / xs);
       const int nck = (ns + 3) / 4 > 65535 ? 65535 : (ns + 3) / 4;
@@ -930,7 +912,7 @@ extern "C" int ffsr_dw3x3_gate_pool_f32(const float* in, int ldi, const float* w
   // measured (tools/dw_bench.py, strips of >= 8192 waves): wins on the widest level (64 channels: 506 vs 1065 us at 1408 x 2048,
   // 257 vs 288 us at 1024 x 1024); from 128 channels on the run kernel's 5 waves per SIMD x 36 loads in flight are as fast or
   // faster (352 x 512 x 256: 200 vs 325 us)
-  if (dw3x3_strip_enabled() && C <= dw3x3_strip_maxc() && (long long)H * W >= 65536 && W >= 64 && (long long)B * H * W * (ldi > ldo ? ldi : ldo) < (1ll << 31))     // (any nchunk: a workgroup walks the strips chunk * 4 + wave, + 4 nchunk, ...)
+  if (C <= DW3X3_STRIP_MAXC && (long long)H * W >= 65536 && W >= 64 && (long long)B * H * W * (ldi > ldo ? ldi : ldo) < (1ll << 31))     // (any nchunk: a workgroup walks the strips chunk * 4 + wave, + 4 nchunk, ...)
     FFSR_LAUNCH(dw3x3_strip_kernel<true>, dim3((C + 63) / 64, nchunk, B), dim3(256), 0, ST, in, ldi, w, bias, out, ldo, part,
                        H, W, C, nchunk, 0, dw3x3_strip_width(H, W, (C + 63) / 64, B));
   else

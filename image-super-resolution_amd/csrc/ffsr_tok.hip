@@ -967,14 +967,14 @@ int tok_chain_common(const float* x, int ldx, const void* w1, const float* b1, c
       return FFSR_EINVAL;
     }
     if (!a.res_is_x) return (ks1 == 6 && nt2 == 12) ? launch_tok_w<6, 12, 0, false, 6>(a, waves, st) : FFSR_EINVAL;   // GRL: C = 180
-#define FFSR_TOK_HEAD_CASE(KS, NT) \
+#define FFSR_HEAD_CHAIN_CASE(KS, NT) \
   if (ks1 == KS && nt2 == NT) return launch_tok_w<KS, NT, 0, true, KS>(a, waves, st)
-    FFSR_TOK_HEAD_CASE(6, 12);
-    FFSR_TOK_HEAD_CASE(7, 14);
-    FFSR_TOK_HEAD_CASE(8, 16);
-    FFSR_TOK_HEAD_CASE(9, 18);
-    FFSR_TOK_HEAD_CASE(10, 20);
-#undef FFSR_TOK_HEAD_CASE
+    FFSR_HEAD_CHAIN_CASE(6, 12);
+    FFSR_HEAD_CHAIN_CASE(7, 14);
+    FFSR_HEAD_CHAIN_CASE(8, 16);
+    FFSR_HEAD_CHAIN_CASE(9, 18);
+    FFSR_HEAD_CHAIN_CASE(10, 20);
+#undef FFSR_HEAD_CHAIN_CASE
     return FFSR_EINVAL;
   }
 #define FFSR_TOK_CASE(KS, NT, MD)                                                       \

@@ -11,10 +11,6 @@ from . import ops
 from .common import SRTail, dev, to_map, tokens
 from .ops import ACT_GELU, ACT_LRELU
 
-import os
-
-TAIL_FUSED = os.environ.get("FFSR_TOK_TAIL", "1") != "0"   # FFSR_TOK_TAIL=0: adjust convolutions as their own launches (A/B runs)
-
 
 class _Swin:
     def __init__(self, sd, p, device, dim, heads, ws, shift):
@@ -43,25 +39,27 @@ class _Swin:
     def __call__(self, x, B, H, W, tail=None):
         """x [P, dim] (row stride may be wider) -> [P, dim]; tail (see ops.tok_chain): the dense block's adjust convolution rides
         in the MLP kernel and the block's own output is not stored -> returns None"""
-        pl = ops.PLANES_AUTO and ops.GEMM_MODE == "bf16x3"   # LN / fc1 results go to the GEMMs as bf16 hi/lo planes
-        if self.qkv_t is not None and ops.tok_enabled():
+        split = ops.split_mode()
+        # (the token kernels are instantiated for some widths only: the others take LayerNorm + GEMM launches, with the LN / fc1
+        # results as bf16 hi/lo planes in split mode)
+        if self.qkv_t is not None and split:
             qkv = ops.tok_gemm(x, self.qkv_t)
         else:
-            n = ops.layernorm(x, *self.n1, out_planes=True, want_f32=False) if pl else ops.layernorm(x, *self.n1)
+            n = ops.layernorm(x, *self.n1, out_planes=True, want_f32=False) if split else ops.layernorm(x, *self.n1)
             qkv = ops.linear(n, self.qkv)
         a = ops.window_attn(qkv, self.bias, B, H, W, self.dim, self.heads, self.ws, self.shift, self.scale)
-        if self.proj_t is not None and ops.tok_enabled() and ops.HEAD_FUSED:
+        if self.proj_t is not None and split:
             if tail is not None:
                 ops.tok_head_chain(a, self.proj_t, self.mlp, hres=x, tail=tail, want_f32=False)
                 return None
             return ops.tok_head_chain(a, self.proj_t, self.mlp, hres=x)
         y = ops.linear(a, self.proj, res=x)
-        if self.mlp is not None and ops.tok_enabled():
+        if self.mlp is not None and split:
             if tail is not None:
                 ops.tok_chain(y, self.mlp, res=y, tail=tail, want_f32=False)
                 return None
             return ops.tok_chain(y, self.mlp, res=y)
-        if not pl:
+        if not split:
             h = ops.linear(ops.layernorm(y, *self.n2), self.fc1, act=ACT_GELU)
             return ops.linear(h, self.fc2, res=y)
         h = ops.linear(ops.layernorm(y, *self.n2, out_planes=True, want_f32=False), self.fc1, act=ACT_GELU,
@@ -101,7 +99,7 @@ class DRCT:
         wide = E + 4 * gc
         cat = [torch.empty(P, wide, device=lr.device), torch.empty(P, wide, device=lr.device)]
         ops.layernorm(tokens(x0), *self.pe_norm, out=cat[0][:, :E])
-        cur = 0
+        cur, split = 0, ops.split_mode()
         for blocks in self.groups:
             buf = cat[cur]
             for j, (sw, adj, adj_t) in enumerate(blocks):
@@ -109,14 +107,14 @@ class DRCT:
                 # the adjust convolution of the dense block as the tail of the Swin block's MLP kernel: the block output itself
                 # (only consumed by adjust) never reaches HBM.  adjust1-4: LeakyReLU(0.2) -> the 32 new channels of the
                 # concatenation; adjust5: x5 * 0.2 + x -> the next group's buffer  (drct_arch.py:292-301)
-                if adj_t is not None and sw.mlp is not None and ops.tok_enabled() and TAIL_FUSED:
+                if adj_t is not None and sw.mlp is not None and split:
                     if j < 4:
                         sw(buf[:, :dim], B, H, W, tail=dict(tg=adj_t, out=buf[:, dim:dim + gc], act=ACT_LRELU, slope=0.2))
                     else:
                         sw(buf[:, :dim], B, H, W, tail=dict(tg=adj_t, out=cat[1 - cur][:, :E], cscale=0.2, res=buf[:, :E]))
                     continue
                 y = sw(buf[:, :dim], B, H, W)
-                if j < 4 and adj_t is not None and ops.tok_enabled():
+                if j < 4 and adj_t is not None and split:        # (a width without an MLP kernel)
                     ops.tok_gemm(y, adj_t, act=ACT_LRELU, slope=0.2, out=buf[:, dim:dim + gc])
                 elif j < 4:
                     ops.linear(y, adj, act=ACT_LRELU, slope=0.2, out=buf[:, dim:dim + gc])

@@ -71,13 +71,15 @@ class _MHA:
         E = sd[p + "in_proj_weight"].shape[1]
         self.inp_t = ops.pack_tok_gemm(sd[p + "in_proj_weight"], sd[p + "in_proj_bias"], device, ln=ln) \
             if ln is not None and ops.tok_gemm_ok(E, 3 * E) else None
-        self.ln_fused = self.inp_t is not None
         self.out = ops.pack_conv(sd[p + "out_proj.weight"], sd[p + "out_proj.bias"], device)
         self.E = self.out.N
 
+    def ln_fused(self) -> bool:
+        return self.inp_t is not None and ops.split_mode()
+
     def __call__(self, normed, resid, S, T):
-        """normed: the LayerNorm-ed tokens -- or, with `ln_fused`, the raw tokens (the norm rides in the in_proj kernel)"""
-        if self.inp_t is not None and self.ln_fused and ops.tok_enabled():
+        """normed: the LayerNorm-ed tokens -- or, when `ln_fused()`, the raw tokens (the norm rides in the in_proj kernel)"""
+        if self.ln_fused():
             qkv = ops.tok_gemm(normed, self.inp_t)
         else:
             qkv = ops.linear(normed, self.inp)
@@ -242,8 +244,7 @@ class FusionNet:
         P = B * h * w
         rows = bands.reshape(P * 9, 4)
         proj = ops.linear(rows, self.band_proj)                                     # [P*9, 64]
-        fused = self.cb_mha.ln_fused and ops.tok_enabled()
-        attn = self.cb_mha(proj if fused else ops.layernorm(proj, *self.cb_norm), proj, P, 9)          # + residual
+        attn = self.cb_mha(proj if self.cb_mha.ln_fused() else ops.layernorm(proj, *self.cb_norm), proj, P, 9)          # + residual
         routing = None
         for i in range(3):
             feat = attn.as_strided((B, h, w, 64), (h * w * 576, w * 576, 576, 1), attn.storage_offset() + 64 * i)
@@ -260,9 +261,8 @@ class FusionNet:
         for e, n in enumerate(EXPERTS):
             view = st.as_strided((B, h, w, 128), (h * w * 512, w * 512, 512, 1), 128 * e)
             ops.conv2d(feats[n], self.align[n], out=view)
-        fused = self.co_mha.ln_fused and ops.tok_enabled()
-        s1 = self.co_mha(st if fused else ops.layernorm(st, *self.co_n1), st, P, 4)
-        if self.co_ffn is not None and ops.tok_enabled():
+        s1 = self.co_mha(st if self.co_mha.ln_fused() else ops.layernorm(st, *self.co_n1), st, P, 4)
+        if self.co_ffn is not None and ops.split_mode():
             s2 = ops.tok_chain(s1, self.co_ffn, res=s1)
         else:
             hdn = ops.linear(ops.layernorm(s1, *self.co_n2), self.co_f0, act=ACT_GELU)
@@ -367,7 +367,7 @@ class FusionNet:
         else:                                                   # simple_fusion: 1x1 conv over the 12 stacked channels (:748-750)
             hier = ops.conv2d(enh, self.simple)
             ops.fusion_route(enh, hier, routing, None, gates, diff, fused)
-        if ops.PLANES_AUTO and ops.GEMM_MODE == "bf16x3":   # the whole 6-conv stack runs on bf16 hi/lo planes
+        if ops.split_mode():   # the whole 6-conv stack runs on bf16 hi/lo planes
             r = ops.split_planes(fused[..., :3])
             thin = ops.thin3_ok(self.refine[-1], B * Hh * Wh)        # the 128 -> 3 head reads an fp32 map
             for i, cv in enumerate(self.refine[:-1]):

@@ -9,8 +9,6 @@ being rebuilt on the CPU and copied per image (grl_arch.py:431-453).
 """
 from __future__ import annotations
 
-import os
-
 import math
 
 import torch
@@ -51,9 +49,6 @@ def _cpb_bias_T(sd, p, table, index, device):
     return dev(b.permute(2, 1, 0), device), dev(logit, device)
 
 
-QKV_TOK = os.environ.get("FFSR_GRL_QKV_TOK", "1") != "0"
-
-
 class _Block:
     def __init__(self, sd, p, device, dim, heads, window_shift):
         self.dim, self.heads, self.hd = dim, heads, dim // 2 // heads
@@ -62,7 +57,7 @@ class _Block:
         self.qkv = ops.pack_conv(sd[a + "qkv.body.weight"], sd[a + "qkv.body.bias"], device)
         # qkv on the token GEMM (rows in registers, no LayerNorm: GRL is post-norm) instead of the planes tile kernel
         self.qkv_t = ops.pack_tok_gemm(sd[a + "qkv.body.weight"], sd[a + "qkv.body.bias"], device) \
-            if QKV_TOK and ops.tok_gemm_ok(dim, 3 * dim) else None
+            if ops.tok_gemm_ok(dim, 3 * dim) else None
         self.anchor = ops.pack_conv(sd[a + "anchor.body.0.reduction.weight"], sd[a + "anchor.body.0.reduction.bias"], device)
         self.proj = ops.pack_conv(sd[a + "proj.weight"], sd[a + "proj.bias"], device)
         AW = WS // DF
@@ -88,9 +83,9 @@ class _Block:
         """x [P, dim] contiguous tokens (xp: the same tensor as bf16 hi/lo planes, if the producer emitted them)
         -> ([P, dim], planes of it or None)"""
         C, hd, heads = self.dim, self.hd, self.heads
-        pl = ops.PLANES_AUTO and ops.GEMM_MODE == "bf16x3"
+        split = ops.split_mode()
         xm = to_map(x, B, H, W)
-        if self.qkv_t is not None and ops.tok_enabled():
+        if self.qkv_t is not None and split:
             qkv = ops.tok_gemm(x, self.qkv_t)                              # [P, 3C]: window half | stripe half
         else:
             qkv = ops.linear(xp if xp is not None else x, self.qkv)
@@ -98,17 +93,18 @@ class _Block:
         cat = torch.empty(x.shape[0], C, device=x.device)
         ops.grl_window_attn(qkv, 0, self.bw, self.lw, cat, 0, B, H, W, heads, hd, self.shift)
         ops.grl_stripe_attn(qkv, 3 * C // 2, anchor, self.b1, self.b2, self.l1, self.l2, cat, C // 2, B, H, W, heads, hd)
-        c2, att = self.cab(xp.reshape_map(B, H, W) if (pl and xp is not None) else xm)
-        if pl and self.proj_t is not None and ops.tok_enabled() and ops.HEAD_FUSED:
+        c2, att = self.cab(xp.reshape_map(B, H, W) if xp is not None else xm)
+        if self.proj_t is not None and split:
             return ops.tok_head_chain(cat, self.proj_t, self.mlp, head_ln=self.n1, hres=x, hres2=tokens(c2), hvec2=att,
                                       rows_per_batch=H * W, post_ln=self.n2, out_planes=True)
         a = ops.linear(cat, self.proj)
         # y = x + LN(attn(x)) + CAB(x): the channel-attention scaling of CAB (c2 * att[batch]) rides in the LN kernel
-        if not pl:
+        if not split:
             y = ops.layernorm(a, *self.n1, res1=x, res2=tokens(c2), res2_vec=att, rows_per_batch=H * W)
             m = ops.linear(ops.linear(y, self.fc1, act=ACT_GELU), self.fc2)
             return ops.layernorm(m, *self.n2, res1=y), None
-        if self.mlp is not None and ops.tok_enabled():
+        # split mode, a width without the head kernel (tok_head_ok) or without an MLP kernel
+        if self.mlp is not None:
             y = ops.layernorm(a, *self.n1, res1=x, res2=tokens(c2), res2_vec=att, rows_per_batch=H * W)
             return ops.tok_chain(y, self.mlp, post_ln=self.n2, res2=y, out_planes=True)
         y, yp = ops.layernorm(a, *self.n1, res1=x, res2=tokens(c2), res2_vec=att, rows_per_batch=H * W, out_planes=True)

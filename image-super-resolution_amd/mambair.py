@@ -8,8 +8,6 @@ is one fused row kernel.
 """
 from __future__ import annotations
 
-import os
-
 import torch
 
 from . import ops
@@ -34,10 +32,7 @@ class _VSS:
         xw = sd[s + "x_proj_weight"].float()                                  # [4, R+2N, Dm]
         self.R = xw.shape[1] - 32
         self.x_proj = ops.pack_conv(xw.reshape(-1, xw.shape[2]), None, device)  # [4*(R+2N), Dm]
-        # (FFSR_TOK_XPROJ=1: x_proj on the token GEMM -- measured 156 us against 158 us for the f32-input tile kernel: not adopted)
-        xw2 = xw.reshape(-1, xw.shape[2])
-        self.x_proj_t = ops.pack_tok_gemm(xw2, None, device) \
-            if os.environ.get("FFSR_TOK_XPROJ", "0") == "1" and ops.tok_gemm_ok(xw2.shape[1], xw2.shape[0]) else None
+        # (x_proj on the token GEMM measured 156 us against 158 us for the f32-input tile kernel: not adopted)
         self.dtw = dev(sd[s + "dt_projs_weight"], device)                     # [4, Dm, R]
         self.dtb = dev(sd[s + "dt_projs_bias"], device)                       # [4, Dm]
         self.A = dev(-torch.exp(sd[s + "A_logs"].float()), device)            # [4*Dm, 16]
@@ -52,31 +47,27 @@ class _VSS:
     def __call__(self, x, B, H, W):
         """x [P, C] tokens -> [P, C]"""
         Dm = self.Dm
-        pl = ops.PLANES_AUTO and ops.GEMM_MODE == "bf16x3"
-        if self.in_proj_t is not None and ops.tok_enabled():
+        split = ops.split_mode()
+        # (the token kernels exist for some widths only: in_proj_t / out_proj_t are None for the others)
+        if self.in_proj_t is not None and split:
             xz = ops.tok_gemm(x, self.in_proj_t)                              # [P, 2*Dm] = x | z
         else:
-            n1 = ops.layernorm(x, *self.ln1, out_planes=True, want_f32=False) if pl else ops.layernorm(x, *self.ln1)
+            n1 = ops.layernorm(x, *self.ln1, out_planes=True, want_f32=False) if split else ops.layernorm(x, *self.ln1)
             xz = ops.linear(n1, self.in_proj)
         u = ops.dwconv2d(to_map(xz[:, :Dm], B, H, W), self.dw, act=ACT_SILU)  # [B,H,W,Dm]
         ut = tokens(u)
-        if self.x_proj_t is not None and ops.tok_enabled():
-            xdbl = ops.tok_gemm(ut, self.x_proj_t)                            # [P, 4*(R+32)]
-        else:
-            xdbl = ops.linear(ut, self.x_proj)
-        fused_proj = pl and self.out_proj_t is not None and ops.tok_enabled() and ops.PROJ_FUSED
-        y4 = ops.selective_scan4(ut, xdbl, self.dtw, self.dtb, self.A, self.Ds, B, H, W, Dm, self.R,
-                                 pairs=False if fused_proj else None)
-        if fused_proj:
+        xdbl = ops.linear(ut, self.x_proj)                                    # [P, 4*(R+32)]
+        y4 = ops.selective_scan4(ut, xdbl, self.dtw, self.dtb, self.A, self.Ds, B, H, W, Dm, self.R)
+        if self.out_proj_t is not None and split:
             # (4-wave workgroups: the 12-k-step rows need ~440 registers, two waves per SIMD would spill)
             y, n2 = ops.tok_proj(y4[0], self.out_proj_t, xdirs=4, xstride=y4.stride(0), z=xz[:, Dm:], pro_ln=self.out_norm,
                                  res=x, rvec=self.skip1, post_ln=self.ln2, out_pre_ln=True, out_planes=True,
                                  waves=ops.TOK_WAVES or 4)
             c2, att = self.cab(n2.reshape_map(B, H, W))
             return ops.scale_add(y, tokens(c2), avec=self.skip2, bvec=att, rows_per_batch=H * W)
-        g = ops.mamba_norm_gate(y4, xz[:, Dm:], *self.out_norm, out_planes=True if pl else None, want_f32=not pl)
+        g = ops.mamba_norm_gate(y4, xz[:, Dm:], *self.out_norm, out_planes=True if split else None, want_f32=not split)
         y = ops.linear(g, self.out_proj, res=x, rvec=self.skip1)              # x * skip_scale + out_proj(LN(sum y) * silu(z))
-        if pl:
+        if split:
             c2, att = self.cab(ops.layernorm(y, *self.ln2, out_planes=True, want_f32=False).reshape_map(B, H, W))
         else:
             c2, att = self.cab(to_map(ops.layernorm(y, *self.ln2), B, H, W))

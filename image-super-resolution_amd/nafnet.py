@@ -7,15 +7,13 @@ reference's forward hook captures, expert_loader.py:553-558).
 """
 from __future__ import annotations
 
-import os
-
 import torch
 
 from . import ops
 from .common import dev, to_map, tokens
 
 
-CONV1_TOK_MAXC = int(os.environ.get("FFSR_NAF_CONV1_TOK_MAXC", "256"))   # norm1 + conv1 on the token GEMM up to this width
+CONV1_TOK_MAXC = 256   # norm1 + conv1 on the token GEMM up to this width
 
 
 class _Block:
@@ -68,8 +66,10 @@ class _Block:
         c = self.c
         # deep levels (c >= 256: long K, few pixels) are MFMA-heavy: their LayerNorm outputs go to the GEMM as bf16
         # hi/lo planes; the shallow levels are HBM-bound either way and keep the fp32 path
-        pl = ops.PLANES_AUTO and ops.GEMM_MODE == "bf16x3" and c >= 256
-        if self.conv1_t is not None and ops.tok_enabled() and ops.rows(x) > 64 * 24:
+        split = ops.split_mode()
+        pl = split and c >= 256
+        # (the token kernels only pay above 64 * 24 rows, and exist for some widths only: the rest takes LayerNorm + GEMM)
+        if self.conv1_t is not None and split and ops.rows(x) > 64 * 24:
             Bx, Hx, Wx, _ = x.shape
             t = to_map(ops.tok_gemm(tokens(x), self.conv1_t), Bx, Hx, Wx)
         else:
@@ -77,21 +77,21 @@ class _Block:
             t = ops.conv2d(t, self.conv1)
         g, pooled = ops.dw3x3_gate_pool(t, self.dw)              # SimpleGate + global average pool
         sca = ops.linear(pooled, self.sca)                       # [B, c] channel attention
-        if self.conv3_t is not None and ops.tok_enabled() and ops.HEAD_FUSED and ops.rows(x) > 64 * 24:
+        if self.conv3_t is not None and split and ops.rows(x) > 64 * 24:
             B, H, W, _ = x.shape
             return to_map(ops.tok_head_chain(tokens(g), self.conv3_t, self.ffn, in_scale=sca.contiguous(), hres=tokens(x),
                                              rows_per_batch=H * W), B, H, W)
         y = ops.conv2d(g, self.conv3, akscale=sca.contiguous(), res=x, cvec=self.beta)   # x + conv3(g*sca)*beta
         B, H, W, _ = y.shape
-        if self.ffn is not None and ops.tok_enabled() and B * H * W > 64 * 24:
+        if self.ffn is not None and split and B * H * W > 64 * 24:
             yt = tokens(y)
             return to_map(ops.tok_chain(yt, self.ffn, res=yt), B, H, W)
-        if self.conv4_t is not None and ops.tok_enabled() and B * H * W > 64 * 24:
+        if self.conv4_t is not None and split and B * H * W > 64 * 24:
             t = to_map(ops.tok_gemm(tokens(y), self.conv4_t), B, H, W)
             g = ops.mul_add(t[..., :c], t[..., c:])              # SimpleGate
             return ops.conv2d(g, self.conv5, res=y, cvec=self.gamma)
         t = ops.layernorm(y, *self.n2, eps=1e-6, out_planes=True if pl else None, want_f32=not pl)
-        if self.conv4g is not None and ops.GEMM_MODE == "bf16x3" and ops.GATE_FUSED and B * H * W > 64 * 24:
+        if self.conv4g is not None and split and B * H * W > 64 * 24:
             g = ops.conv2d(t, self.conv4g, gate=True)            # conv4 + SimpleGate in one kernel
         else:
             t = ops.conv2d(t, self.conv4)

@@ -28,17 +28,6 @@ _ENV_MODE = os.environ.get("FFSR_GEMM_MODE", "bf16x3")
 GEMM_MODE = "bf16x3" if _ENV_MODE == "bf16" else _ENV_MODE      # "bf16" = the bf16x3 kernels with one product term (hip.lib() sets it)
 
 
-# Precision-budget experiment: FFSR_WEIGHT_LO=0 packs every weight with a ZERO lo plane, i.e. the split-bf16
-# kernels then evaluate a_hi*w_hi + a_lo*w_hi -- the arithmetic of a 2-term ("bf16x2") mode with bf16-rounded weights -- without
-# touching the kernels.  Measured by tools/precision_budget.py; not a default.
-WEIGHT_LO = os.environ.get("FFSR_WEIGHT_LO", "1") != "0"
-
-
-def set_weight_lo(on: bool):
-    global WEIGHT_LO
-    WEIGHT_LO = bool(on)
-
-
 BN128_MIN_N = 1 << 30   # the 128-column tile (2 waves/SIMD) measured slower on every shape: keep BN = 64
 
 
@@ -56,6 +45,11 @@ def set_gemm_mode(mode: str):
     hip.call("ffsr_set_gemm_terms", GEMM_TERMS)
 
 
+def split_mode() -> bool:
+    """split-bf16 mode: the fused token kernels and the bf16 planes paths belong to it; f32 mode takes the plain kernels"""
+    return GEMM_MODE == "bf16x3"
+
+
 def gemm_mode_name() -> str:
     return "bf16" if (GEMM_MODE == "bf16x3" and GEMM_TERMS == 1) else GEMM_MODE
 
@@ -63,6 +57,29 @@ def gemm_mode_name() -> str:
 # bench.py sets this to a list to time every conv/GEMM launch with events on the launch stream:
 # entries (start_event, end_event, algorithmic flops = 2 * M * N * KH*KW*Cin with the UNPADDED Cin, shape + kernel kind, bytes)
 CONV_PROFILE = None
+
+
+def _prof_begin():
+    """start event of a CONV_PROFILE entry (None when nothing is being profiled)"""
+    if CONV_PROFILE is None:
+        return None
+    e0 = torch.cuda.Event(enable_timing=True)
+    e0.record()
+    return e0
+
+
+def _prof_end(e0, flops, shape, nbytes):
+    if e0 is not None:
+        e1 = torch.cuda.Event(enable_timing=True)
+        e1.record()
+        CONV_PROFILE.append((e0, e1, flops, shape, nbytes))
+
+
+def _outputs(out, planes):
+    """what an op with an optional second (planes) output returns: out, planes, or (out, planes)"""
+    if planes is None:
+        return out
+    return planes if out is None else (out, planes)
 
 
 def _stream():
@@ -232,15 +249,14 @@ def pack_conv(w: torch.Tensor, b: Optional[torch.Tensor], device, stride=1, pad=
     lo = torch.zeros(Np, Kp, dtype=torch.bfloat16, device=device)
     h = w2.to(torch.bfloat16)
     hi[:N, :w2.shape[1]] = h
-    if WEIGHT_LO:
-        lo[:N, :w2.shape[1]] = (w2 - h.float()).to(torch.bfloat16)
+    lo[:N, :w2.shape[1]] = (w2 - h.float()).to(torch.bfloat16)
     # planes path: every tap padded to a multiple of 32 channels, rows padded to x768 (any column tile of 64/128/192/256)
     C32, Np3 = pad32(Cin), (N + 767) // 768 * 768
     w3 = torch.zeros(Np3, KH, KW, C32, dtype=torch.float32, device=device)
     w3[:N, :, :, :Cin] = wt
     w3 = w3.reshape(Np3, KH * KW * C32)
     ph = w3.to(torch.bfloat16)
-    pl = (w3 - ph.float()).to(torch.bfloat16) if WEIGHT_LO else torch.zeros_like(ph)
+    pl = (w3 - ph.float()).to(torch.bfloat16)
     return Conv(w2, None if b is None else b.detach().float().contiguous().to(device), N, Cp, KH, KW, stride,
                 pad, Cin, hi, lo, ph, pl, C32)
 
@@ -255,17 +271,13 @@ def zero_page(device) -> torch.Tensor:
     return _ZEROS[key]
 
 
-GATE_FUSED = os.environ.get("FFSR_GATE_FUSED", "1") != "0"   # FFSR_GATE_FUSED=0: NAFNet's conv4 and SimpleGate stay separate (A/B runs)
-STRIP3 = os.environ.get("FFSR_STRIP3", "1") != "0"   # FFSR_STRIP3=0: 3x3 convs stay on the per-tap tile kernel (A/B runs)
-
-
 def planes_tile(M: int, N: int, K: int, conv3: bool = False):
     """(bm, bn, stages) of the planes GEMM (measured on MI355X, tools/planes_bench.py): least padded N weighted by the
     tile's efficiency (192 > 128 > 64 columns); 256-row tiles only pay on long-K shapes with many row tiles.
     conv3 (3x3, stride 1, pad 1): the tap-strip variant (stages 4; 64- / 128-column tiles) where it measured faster
     (tools/strip_bench.py: N = 45 / 60 at Cin 180: 200 / 214 -> 134 / 153 us; 128 -> 128 at HR: 2394 -> 2309 us; with
     N = 180 the 192-column per-tap tile stays ahead)."""
-    if conv3 and STRIP3 and M >= 16384:
+    if conv3 and M >= 16384:
         if N <= 64:
             return 128, 64, 4
         if N <= 128 and K >= 512:
@@ -282,7 +294,6 @@ def planes_tile(M: int, N: int, K: int, conv3: bool = False):
 
 
 PLANES_ACTS = (ACT_NONE, ACT_GELU, ACT_RELU, ACT_LRELU)
-THIN3 = os.environ.get("FFSR_THIN3", "1") != "0"   # FFSR_THIN3=0: the N <= 4 3x3 heads stay on the GEMM kernels (A/B runs)
 
 
 def thin3_ok(cv: "Conv", M: int, x: Optional[torch.Tensor] = None) -> bool:
@@ -290,12 +301,11 @@ def thin3_ok(cv: "Conv", M: int, x: Optional[torch.Tensor] = None) -> bool:
     32-column MFMA tile that is 7/8 padding.  x (the input map, if known): the kernel reads 16-byte vectors, so the pixel
     stride must be a multiple of 4 and the first pixel 16-byte aligned -- a channel-slice view at an odd offset takes the
     GEMM kernels instead."""
-    ok = (THIN3 and cv.KH == 3 and cv.KW == 3 and cv.stride == 1 and cv.pad == 1 and cv.N <= 4
+    ok = (cv.KH == 3 and cv.KW == 3 and cv.stride == 1 and cv.pad == 1 and cv.N <= 4
           and cv.Cin in (8, 16, 32, 64, 128) and cv.N <= cv.Cin // 4 and M >= 4096)
     if ok and x is not None:
         ok = ld(x) % 4 == 0 and x.data_ptr() % 16 == 0 and ld(x) >= cv.Cin and rows(x) * ld(x) * 4 < 2 ** 32
     return ok
-PLANES_AUTO = os.environ.get("FFSR_PLANES", "1") != "0"   # FFSR_PLANES=0: every GEMM takes its fp32 input directly
 
 
 def conv2d(x, cv: Conv, *, act=ACT_NONE, slope=0.0, out: Optional[torch.Tensor] = None,
@@ -327,10 +337,10 @@ def conv2d(x, cv: Conv, *, act=ACT_NONE, slope=0.0, out: Optional[torch.Tensor] 
                  0 if res is None else ld(res), B, H, W, cv.Cin, cv.N, act, float(slope), float(cscale), float(rscale), _stream())
         return out
     if gate:
-        if is_planes or GEMM_MODE != "bf16x3" or shuffle or act != ACT_NONE or cv.N % 64 or B * Ho * Wo <= 64 * 24:
+        if is_planes or not split_mode() or shuffle or act != ACT_NONE or cv.N % 64 or B * Ho * Wo <= 64 * 24:
             raise ValueError("gate=True needs an fp32 map input, the split-bf16 mode, no activation and N % 64 == 0")
         shuffle, tile_hint = 3, 128           # store mode 3 of ffsr_conv2d_bf16x3
-    if (not is_planes and PLANES_AUTO and GEMM_MODE == "bf16x3" and not shuffle and akscale is None and tile_hint == 0
+    if (not is_planes and split_mode() and not shuffle and akscale is None and tile_hint == 0
             and act in PLANES_ACTS and cv.KH * cv.KW > 1 and cv.stride == 1 and cv.Cin_true >= 32 and cv.N > 64 and B * Ho * Wo >= 16384):
         # long-K conv on an fp32 map: one extra split pass (read + write of the input) buys the ~1.5x faster planes GEMM
         x = split_planes(widen(x, cv.Cin_true) if x.shape[3] != cv.Cin_true else x)
@@ -348,10 +358,7 @@ def conv2d(x, cv: Conv, *, act=ACT_NONE, slope=0.0, out: Optional[torch.Tensor] 
     if res is not None:
         assert tuple(res.shape) == oshape
         ldr = ld(res)
-    prof = CONV_PROFILE
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    e0 = _prof_begin()
     kernel_kind = 0      # for CONV_PROFILE: 0 fp32-input kernel, 1 planes tile kernel, 2 planes tap-strip kernel
     if is_planes:
         assert x.Cp == cv.Cp32 and x.C == cv.Cin_true, f"planes input {x.shape} (Cp {x.Cp}) vs conv Cin {cv.Cin_true}"
@@ -376,7 +383,7 @@ def conv2d(x, cv: Conv, *, act=ACT_NONE, slope=0.0, out: Optional[torch.Tensor] 
         if akscale is not None:
             assert akscale.shape == (B, cv.Cin) and akscale.is_contiguous()
             akrows = H * W
-        if tile_hint == 0 and GEMM_MODE == "bf16x3" and B * Ho * Wo > 64 * 24 and cv.KH * cv.KW <= 32:
+        if tile_hint == 0 and split_mode() and B * Ho * Wo > 64 * 24 and cv.KH * cv.KW <= 32:
             tile_hint = 32 if cv.N <= 32 else (64 if cv.N <= 64 or BN128_MIN_N > cv.N else 128)
         if tile_hint in (32, 64, 128):
             hip.call("ffsr_conv2d_bf16x3", _ptr(x), _ptr(cv.whi), _ptr(cv.wlo), cv.whi.shape[1], cv.whi.shape[0],
@@ -387,15 +394,11 @@ def conv2d(x, cv: Conv, *, act=ACT_NONE, slope=0.0, out: Optional[torch.Tensor] 
             hip.call("ffsr_conv2d_f32", _ptr(x), _ptr(cv.wgt), _ptr(cv.bias), _ptr(out), _ptr(res), _ptr(cvec), _ptr(rvec),
                      _ptr(akscale), B, H, W, cv.Cin, ldi, cv.N, ld(out), ldr, cv.KH, cv.KW, cv.stride, cv.pad, cv.pad,
                      act, float(slope), float(cscale), float(rscale), shuffle, akrows, tile_hint, _stream())
-    if prof is not None:
-        e1.record()
-        prof.append((e0, e1, 2.0 * B * Ho * Wo * cv.N * cv.KH * cv.KW * cv.Cin_true,
-                     (B * Ho * Wo, cv.N, cv.KH * cv.KW * cv.Cin, cv.KH, kernel_kind),
-                     4.0 * (B * H * W * cv.Cin_true + cv.N * cv.KH * cv.KW * cv.Cin_true
-                            + B * Ho * Wo * cv.N * (2 if res is not None else 1))))
-    if out_planes is not None:
-        return (out, out_planes) if out is not None else out_planes
-    return out
+    _prof_end(e0, 2.0 * B * Ho * Wo * cv.N * cv.KH * cv.KW * cv.Cin_true,
+              (B * Ho * Wo, cv.N, cv.KH * cv.KW * cv.Cin, cv.KH, kernel_kind),
+              4.0 * (B * H * W * cv.Cin_true + cv.N * cv.KH * cv.KW * cv.Cin_true
+                     + B * Ho * Wo * cv.N * (2 if res is not None else 1)))
+    return _outputs(out, out_planes)
 
 
 def linear(x2d, cv: Conv, **kw):
@@ -436,11 +439,11 @@ TOK_SHAPES = {0: ((4, 8), (6, 12), (7, 14), (8, 16), (9, 18), (10, 20)), 1: ((2,
 
 # k-step counts ffsr_tok_head_chain_f32 is instantiated for: mode 0 (x1 + mlp(norm(x1))), mode 1 (gated chain), "post" (mode 0 with
 # the post-LayerNorm form norm(mlp(x1)) + x1)
-TOK_HEAD_KS = {0: (6, 7, 8, 9, 10), 1: (2, 4), "post": (6,)}
+HEAD_CHAIN_KS = {0: (6, 7, 8, 9, 10), 1: (2, 4), "post": (6,)}
 
 
 def tok_head_ok(K: int, mode) -> bool:
-    return K % 4 == 0 and (K + 31) // 32 in TOK_HEAD_KS[mode]
+    return K % 4 == 0 and (K + 31) // 32 in HEAD_CHAIN_KS[mode]
 
 
 def tok_chain_ok(K: int, N: int, mode: int) -> bool:
@@ -449,8 +452,7 @@ def tok_chain_ok(K: int, N: int, mode: int) -> bool:
 
 def _split_bf16(w: torch.Tensor):
     hi = w.to(torch.bfloat16)
-    lo = (w - hi.float()).to(torch.bfloat16) if WEIGHT_LO else torch.zeros_like(hi)
-    return hi, lo
+    return hi, (w - hi.float()).to(torch.bfloat16)
 
 
 def pack_tok_chain(w1, b1, w2, b2, device, *, mode=0, ln=None, eps=1e-5) -> TokChain:
@@ -568,37 +570,16 @@ def tok_gemm(x2d, tg: TokGemm, *, act=ACT_NONE, slope=0.0, cvec=None, cscale=1.0
         out_planes = Planes(1, 1, M, tg.N, x2d.device)
     if out is None and (want_f32 or out_planes is None):
         out = torch.empty(M, tg.N, device=x2d.device)
-    prof = CONV_PROFILE
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    e0 = _prof_begin()
     hip.call("ffsr_tok_gemm_f32", _ptr(x2d), x2d.stride(0), _ptr(tg.w1), _ptr(tg.b1), _ptr(cvec), _ptr(out),
              0 if out is None else out.stride(0), None if out_planes is None else _ptr(out_planes.hi),
              None if out_planes is None else _ptr(out_planes.lo), 0 if out_planes is None else out_planes.Cp, M, tg.K, tg.N,
              int(tg.pre_ln), tg.eps1, act, float(slope), float(cscale), tok_waves(M, (tg.K + 31) // 32), _stream())
-    if prof is not None:
-        e1.record()
-        prof.append((e0, e1, 2.0 * M * tg.K * tg.N, (M, tg.N, tg.K, 1, 3), 4.0 * (M * tg.K + tg.N * tg.K + M * tg.N)))
-    if out_planes is not None:
-        return (out, out_planes) if out is not None else out_planes
-    return out
+    _prof_end(e0, 2.0 * M * tg.K * tg.N, (M, tg.N, tg.K, 1, 3), 4.0 * (M * tg.K + tg.N * tg.K + M * tg.N))
+    return _outputs(out, out_planes)
 
 
 TOK_WAVES = int(os.environ.get("FFSR_TOK_WAVES", "0"))
-TOK_FUSED = os.environ.get("FFSR_TOK", "1") != "0"   # FFSR_TOK=0: LayerNorm / fc1 / fc2 stay separate launches (A/B runs)
-
-
-HEAD_FUSED = os.environ.get("FFSR_TOK_HEAD", "1") != "0"   # FFSR_TOK_HEAD=0: attention proj (+ residual / LayerNorm) as own launches
-# MambaIR's out_norm + gate + out_proj + skip + ln_2 as ONE kernel (ffsr_tok_proj_f32, 4-wave workgroups); FFSR_TOK_PROJ=0: the three
-# launches it replaces.  History of the measurement (tools/proj_bench.py, 352 x 512 x 360): first version 594 us against 591 us for
-# the three launches (its epilogue waited for every bias / LayerNorm-vector / residual load separately, one exec-masked block per
-# tile); with the batched epilogue loads 492 us against 556 us.
-PROJ_FUSED = os.environ.get("FFSR_TOK_PROJ", "1") != "0"
-
-
-def tok_enabled() -> bool:
-    """the fused token chains replace launches of the split-bf16 mode only (the exact f32 mode keeps the f32-MFMA GEMMs)"""
-    return TOK_FUSED and GEMM_MODE == "bf16x3"
 
 
 def tok_waves(M: int, KS1: int) -> int:
@@ -624,29 +605,21 @@ def tok_chain(x2d, tc: TokChain, *, res=None, rscale=1.0, rvec=None, cvec=None, 
         if out is None and want_f32:
             out = torch.empty(M, tc.N, device=x2d.device)
         r3 = tail.get("res")
-        prof = CONV_PROFILE
-        if prof is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
+        e0 = _prof_begin()
         hip.call("ffsr_tok_chain_tail_f32", _ptr(x2d), x2d.stride(0), _ptr(tc.w1), _ptr(tc.b1), _ptr(tc.w2), _ptr(tc.b2), _ptr(res),
                  0 if res is None else res.stride(0), _ptr(out), 0 if out is None else out.stride(0), M, tc.K, tc.N, tc.steps, tc.mode,
                  int(tc.pre_ln), tc.eps1, _ptr(tg.w1), _ptr(tg.b1), _ptr(r3), 0 if r3 is None else r3.stride(0), _ptr(out3),
                  out3.stride(0), tg.N, tail.get("act", ACT_NONE), float(tail.get("slope", 0.0)), float(tail.get("cscale", 1.0)),
                  float(tail.get("rscale", 1.0)), tok_waves(M, (tc.K + 31) // 32), _stream())
-        if prof is not None:
-            e1.record()
-            prof.append((e0, e1, 2.0 * M * (tc.K * tc.H + tc.H * tc.N + tc.N * tg.N), (M, tc.N, tc.K, 1, 3),
-                         4.0 * (M * tc.K + tc.H * tc.K + tc.N * tc.H + tg.N * tc.N + M * tg.N * (1 + (r3 is not None))
-                                + (M * tc.N if out is not None else 0))))
-        return out3 if out is None else (out, out3)
+        _prof_end(e0, 2.0 * M * (tc.K * tc.H + tc.H * tc.N + tc.N * tg.N), (M, tc.N, tc.K, 1, 3),
+                  4.0 * (M * tc.K + tc.H * tc.K + tc.N * tc.H + tg.N * tc.N + M * tg.N * (1 + (r3 is not None))
+                         + (M * tc.N if out is not None else 0)))
+        return _outputs(out, out3)
     if out_planes is True:
         out_planes = Planes(1, 1, M, tc.N, x2d.device)
     if out is None and (want_f32 or out_planes is None):
         out = torch.empty(M, tc.N, device=x2d.device)
-    prof = CONV_PROFILE
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    e0 = _prof_begin()
     g2, be2 = post_ln if post_ln is not None else (None, None)
     hip.call("ffsr_tok_chain_f32", _ptr(x2d), x2d.stride(0), _ptr(tc.w1), _ptr(tc.b1), _ptr(tc.w2), _ptr(tc.b2), _ptr(cvec),
              _ptr(res), 0 if res is None else res.stride(0), _ptr(rvec), _ptr(g2), _ptr(be2), _ptr(res2),
@@ -654,14 +627,10 @@ def tok_chain(x2d, tc: TokChain, *, res=None, rscale=1.0, rvec=None, cvec=None, 
              None if out_planes is None else _ptr(out_planes.hi), None if out_planes is None else _ptr(out_planes.lo),
              0 if out_planes is None else out_planes.Cp, M, tc.K, tc.N, tc.steps, tc.mode, int(tc.pre_ln), tc.eps1, float(eps2),
              float(cscale), float(rscale), tok_waves(M, (tc.K + 31) // 32), _stream())
-    if prof is not None:
-        e1.record()
-        Hc = tc.H if tc.mode == 0 else tc.H // 2
-        prof.append((e0, e1, 2.0 * M * (tc.K * tc.H + Hc * tc.N), (M, tc.N, tc.K, 1, 3),
-                     4.0 * (M * tc.K + tc.H * tc.K + tc.N * Hc + M * tc.N * (1 + (res is not None) + (res2 is not None)))))
-    if out_planes is not None:
-        return (out, out_planes) if out is not None else out_planes
-    return out
+    Hc = tc.H if tc.mode == 0 else tc.H // 2
+    _prof_end(e0, 2.0 * M * (tc.K * tc.H + Hc * tc.N), (M, tc.N, tc.K, 1, 3),
+              4.0 * (M * tc.K + tc.H * tc.K + tc.N * Hc + M * tc.N * (1 + (res is not None) + (res2 is not None))))
+    return _outputs(out, out_planes)
 
 
 def tok_head_chain(a2d, head: TokGemm, tc: TokChain, *, in_scale=None, head_ln=None, eps0=1e-5, hres=None, hres2=None, hvec2=None,
@@ -683,10 +652,7 @@ def tok_head_chain(a2d, head: TokGemm, tc: TokChain, *, in_scale=None, head_ln=N
     g0, be0 = head_ln if head_ln is not None else (None, None)
     g2, be2 = post_ln if post_ln is not None else (None, None)
     r3 = None if tail is None else tail.get("res")
-    prof = CONV_PROFILE
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    e0 = _prof_begin()
     hip.call("ffsr_tok_head_chain_f32", _ptr(a2d), a2d.stride(0), _ptr(in_scale), _ptr(head.w1), _ptr(head.b1), _ptr(g0), _ptr(be0), float(eps0),
              _ptr(hres), 0 if hres is None else hres.stride(0), _ptr(hres2), 0 if hres2 is None else hres2.stride(0), _ptr(hvec2),
              int(rows_per_batch), _ptr(tc.w1), _ptr(tc.b1), _ptr(tc.w2), _ptr(tc.b2), _ptr(g2), _ptr(be2), float(eps2), _ptr(out),
@@ -697,17 +663,11 @@ def tok_head_chain(a2d, head: TokGemm, tc: TokChain, *, in_scale=None, head_ln=N
              0 if tail is None else tail["tg"].N, ACT_NONE if tail is None else tail.get("act", ACT_NONE),
              0.0 if tail is None else float(tail.get("slope", 0.0)), 1.0 if tail is None else float(tail.get("cscale", 1.0)),
              1.0 if tail is None else float(tail.get("rscale", 1.0)), tok_waves(M, (tc.K + 31) // 32), _stream())
-    if prof is not None:
-        e1.record()
-        n3 = 0 if tail is None else tail["tg"].N
-        prof.append((e0, e1, 2.0 * M * (tc.K * tc.K + tc.K * tc.H + tc.H * tc.N + tc.N * n3), (M, tc.N, tc.K, 1, 3),
-                     4.0 * (M * tc.K * (1 + (hres is not None) + (hres2 is not None)) + tc.K * tc.K + 2 * tc.H * tc.K + n3 * tc.N
-                            + M * n3 * (1 + (r3 is not None)) + (M * tc.N if out is not None else 0))))
-    if tail is not None:
-        return out3 if out is None else (out, out3)
-    if out_planes is not None:
-        return (out, out_planes) if out is not None else out_planes
-    return out
+    n3 = 0 if tail is None else tail["tg"].N
+    _prof_end(e0, 2.0 * M * (tc.K * tc.K + tc.K * tc.H + tc.H * tc.N + tc.N * n3), (M, tc.N, tc.K, 1, 3),
+              4.0 * (M * tc.K * (1 + (hres is not None) + (hres2 is not None)) + tc.K * tc.K + 2 * tc.H * tc.K + n3 * tc.N
+                     + M * n3 * (1 + (r3 is not None)) + (M * tc.N if out is not None else 0)))
+    return _outputs(out, out3 if tail is not None else out_planes)
 
 
 def tok_proj_ok(K: int, N: int) -> bool:
@@ -727,23 +687,16 @@ def tok_proj(x2d, tg: TokGemm, *, xdirs=1, xstride=0, z=None, pro_ln=None, peps=
         out = torch.empty(M, tg.N, device=x2d.device)
     pg, pb = pro_ln if pro_ln is not None else (None, None)
     g2, be2 = post_ln if post_ln is not None else (None, None)
-    prof = CONV_PROFILE
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    e0 = _prof_begin()
     hip.call("ffsr_tok_proj_f32", _ptr(x2d), int(xstride), int(xdirs), x2d.stride(0), _ptr(z), 0 if z is None else z.stride(0),
              _ptr(pg), _ptr(pb), float(peps), _ptr(tg.w1), _ptr(tg.b1), _ptr(cvec), _ptr(res), 0 if res is None else res.stride(0),
              _ptr(rvec), _ptr(g2), _ptr(be2), float(eps2), _ptr(out), 0 if out is None else out.stride(0), int(out_pre_ln),
              None if out_planes is None else _ptr(out_planes.hi), None if out_planes is None else _ptr(out_planes.lo),
              0 if out_planes is None else out_planes.Cp, M, tg.K, tg.N, float(cscale), float(rscale),
              waves or tok_waves(M, (tg.K + 31) // 32), _stream())
-    if prof is not None:
-        e1.record()
-        prof.append((e0, e1, 2.0 * M * tg.K * tg.N, (M, tg.N, tg.K, 1, 3),
-                     4.0 * (M * tg.K * (xdirs + (z is not None)) + tg.K * tg.N + M * tg.N * (1 + (res is not None)))))
-    if out_planes is not None:
-        return (out, out_planes) if out is not None else out_planes
-    return out
+    _prof_end(e0, 2.0 * M * tg.K * tg.N, (M, tg.N, tg.K, 1, 3),
+              4.0 * (M * tg.K * (xdirs + (z is not None)) + tg.K * tg.N + M * tg.N * (1 + (res is not None))))
+    return _outputs(out, out_planes)
 
 
 # ---------------------------------------------------------------------------------------------- row kernels
@@ -786,14 +739,12 @@ def layernorm(x, gamma, beta, eps=1e-5, out=None, res1=None, res2=None, out_plan
              0 if out is None else _mat(out)[3], None if out_planes is None else _ptr(out_planes.hi),
              None if out_planes is None else _ptr(out_planes.lo), 0 if out_planes is None else out_planes.Cp, _ptr(r1[0]), r1[3],
              _ptr(r2[0]), r2[3], _ptr(res2_vec), rows_per_batch, M, C, _stream())
-    if out_planes is None:
-        return out
-    return (out, out_planes) if out is not None else out_planes
+    return _outputs(out, out_planes)
 
 
 def final_norm(t2d, norm, B, H, W):
-    """Last LayerNorm of a Swin-family body -> the input of conv_after_body: planes (when enabled) or an fp32 map."""
-    if PLANES_AUTO and GEMM_MODE == "bf16x3":
+    """Last LayerNorm of a Swin-family body -> the input of conv_after_body: planes (split-bf16 mode) or an fp32 map."""
+    if split_mode():
         return layernorm(t2d, *norm, out_planes=True, want_f32=False).reshape_map(B, H, W)
     t = layernorm(t2d, *norm)
     s = t.stride(0)
@@ -935,7 +886,7 @@ def window_attn(qkv, bias, B, H, W, C, heads, ws, shift, scale, out=None, varian
     if out is None:
         out = torch.empty(B * H * W, C, device=qkv.device)
     if variant is None:
-        variant = 0 if GEMM_MODE == "bf16x3" else 3
+        variant = 0 if split_mode() else 3
     hip.call("ffsr_window_attn_f32", _ptr(qkv), _mat(qkv)[3], _ptr(bias), _ptr(out), _mat(out)[3], B, H, W, C, heads,
              ws, shift, float(scale), variant, _stream())
     return out
@@ -981,43 +932,31 @@ def scan_chunk(L: int, waves_per_chunk: int = 24) -> int:
     return c
 
 
-# FFSR_SCAN_PAIRS=1: the scan folds its four per-direction outputs into two planes (directions 2 / 3 add to what 0 / 1 wrote).
-# Off by default: measured at 352 x 512 x 360 the consumer gains what the scan loses (norm_gate 330 -> 212 us, scan 1756 -> 1877 us:
-# two half-size launches per pass quantise worse over the 4096 resident waves, and the read-modify-write is not free)
-SCAN_PAIRS = os.environ.get("FFSR_SCAN_PAIRS", "0") == "1"
-
-
-def selective_scan4(u, xdbl, dtw, dtb, A, Dv, B, H, W, Dm, R, chunk=None, pairs=None):
-    """u [B*L, Dm], xdbl [B*L, 4*(R+32)] -> y [4, B*L, Dm] (per-direction outputs in pixel order), or with `pairs` y [2, B*L, Dm] =
-    (y0 + y2, y1 + y3): the second pair of directions is scanned after the first and adds to its planes."""
+def selective_scan4(u, xdbl, dtw, dtb, A, Dv, B, H, W, Dm, R, chunk=None):
+    """u [B*L, Dm], xdbl [B*L, 4*(R+32)] -> y [4, B*L, Dm] (per-direction outputs in pixel order)"""
     L = H * W
-    pairs = (SCAN_PAIRS and L >= 16384) if pairs is None else pairs
-    nk = 2 if pairs else 4
-    chunk = chunk or scan_chunk(L, nk * B * ((Dm + 63) // 64))
+    chunk = chunk or scan_chunk(L, 4 * B * ((Dm + 63) // 64))
     nchunk = (L + chunk - 1) // chunk
-    y = torch.empty(nk, B * L, Dm, device=u.device)
-    hstate = torch.empty(B, nk, nchunk, Dm, 16, device=u.device)
+    y = torch.empty(4, B * L, Dm, device=u.device)
+    hstate = torch.empty(B, 4, nchunk, Dm, 16, device=u.device)
     decay = torch.empty_like(hstate)
-    hip.call("ffsr_selective_scan4_pairs_f32" if pairs else "ffsr_selective_scan4_f32", _ptr(u), _mat(u)[3], _ptr(xdbl), _mat(xdbl)[3], _ptr(dtw), _ptr(dtb), _ptr(A),
+    hip.call("ffsr_selective_scan4_f32", _ptr(u), _mat(u)[3], _ptr(xdbl), _mat(xdbl)[3], _ptr(dtw), _ptr(dtb), _ptr(A),
              _ptr(Dv), _ptr(y), Dm, _ptr(hstate), _ptr(decay), B, H, W, Dm, R, 16, chunk, _stream())
     return y
 
 
 def mamba_norm_gate(y4, z, gamma, beta, eps=1e-5, out=None, out_planes=None, want_f32=True):
-    """y4 [4, M, C] (or the [2, M, C] pair planes of selective_scan4), z [M, C] (row stride ldz) -> LayerNorm(sum_k y4[k]) * silu(z);
-    out_planes as in layernorm()."""
+    """y4 [4, M, C], z [M, C] (row stride ldz) -> LayerNorm(sum_k y4[k]) * silu(z); out_planes as in layernorm()."""
     nd, M, C = y4.shape
-    assert nd in (2, 4)
+    assert nd == 4
     if out_planes is True:
         out_planes = Planes(1, 1, M, C, y4.device)
     if out is None and (want_f32 or out_planes is None):
         out = torch.empty(M, C, device=y4.device)
-    hip.call("ffsr_mamba_norm_gate_planes_f32" if nd == 4 else "ffsr_mamba_norm_gate_pairs_f32", _ptr(y4), M * C, C, _ptr(z), _mat(z)[3], _ptr(gamma), _ptr(beta), float(eps),
+    hip.call("ffsr_mamba_norm_gate_planes_f32", _ptr(y4), M * C, C, _ptr(z), _mat(z)[3], _ptr(gamma), _ptr(beta), float(eps),
              _ptr(out), 0 if out is None else _mat(out)[3], None if out_planes is None else _ptr(out_planes.hi),
              None if out_planes is None else _ptr(out_planes.lo), 0 if out_planes is None else out_planes.Cp, M, C, _stream())
-    if out_planes is not None:
-        return (out, out_planes) if out is not None else out_planes
-    return out
+    return _outputs(out, out_planes)
 
 
 # ---------------------------------------------------------------------------------------------- fusion specials

@@ -1,7 +1,7 @@
 """VERDICT r1 item 7, the 1-term ("plain bf16") point of the precision budget, estimated on the CPU oracle: every nn.Linear /
 nn.Conv2d of the path evaluated with BOTH operands rounded to bf16 and fp32 accumulation (what a hi*hi-only MFMA mode of
 the GEMM kernels would compute; attention contractions, norms, the scan and everything elementwise stay fp32), against the
-unmodified fp32 oracle.  Same weights / input as tools/precision_budget.py.  usage: python tools/precision_budget_cpu.py"""
+unmodified fp32 oracle.  Weights: random_weights(seed=50), input: a 64x64 LR tile.  usage: python tools/precision_budget_cpu.py"""
 import importlib
 import math
 import os

@@ -12,9 +12,8 @@ for (B,H,W,Cin,N,act,res) in [(1,1360,2040,64,3,0,False),(1,1360,2040,128,3,0,Tr
     r = torch.randn(B,H,W,4,device=dev)[...,:N] if res else None
     cv = ops.pack_conv(w,b,dev)
     slope = 0.2 if act==3 else 0.0
-    def run(thin):
-        ops.THIN3 = thin
-        return ops.conv2d(x, cv, act=act, slope=slope, res=r, cscale=0.1 if res else 1.0)
+    def run(thin):   # thin=False: the split-bf16 GEMM kernel a 32-column tile_hint selects
+        return ops.conv2d(x, cv, act=act, slope=slope, res=r, cscale=0.1 if res else 1.0, tile_hint=0 if thin else 32)
     y1 = run(True); y0 = run(False)
     ref = F.conv2d(x.permute(0,3,1,2).double(), w.double().to(dev), b.double().to(dev), padding=1)
     ref = {0:lambda t:t,1:F.gelu,2:F.relu,3:lambda t:F.leaky_relu(t,0.2),4:torch.sigmoid,5:F.silu}[act](ref)
