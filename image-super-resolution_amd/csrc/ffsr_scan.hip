@@ -25,6 +25,7 @@
 // What is left is the lane-operation count itself: 16 states x (mul, exp2, mul, fma, fma) per (step, channel, direction),
 // twice (pass A and pass C).
 #include "ffsr_common.h"
+#include "ffsr_scan_common.h"
 
 namespace {
 
@@ -50,16 +51,6 @@ __device__ __forceinline__ int tok_pixel(int k, int t, int H, int W, int L) {
     return yy * W + x;
   }
   return t;
-}
-
-// softplus with torch's threshold 20, on the hardware exp2/log2: log1p(e) = e(1 - e(1/2 - e/3)) for small e = exp(x)
-// (relative error < 4e-7), log(1 + e) otherwise.  Branch-free selects.
-__device__ __forceinline__ float softplus_f(float x) {
-  const float e = __builtin_amdgcn_exp2f(fminf(x, 20.f) * 1.4426950408889634f);
-  const float small = e * (1.f - e * (0.5f - e * 0.33333334f));
-  const float big = __builtin_amdgcn_logf(1.f + e) * 0.6931471805599453f;
-  const float sp = e < 0.01f ? small : big;
-  return x > 20.f ? x : sp;
 }
 
 // Steps are processed in groups of G: the group's u values (registers) and projection rows (LDS, wave-uniform reads)
@@ -161,63 +152,6 @@ __global__ __launch_bounds__(64, 4) void scan_chunk_kernel(ScanArgs p) {
     }
   }
 }
-
-// hstate[c] <- state entering chunk c.  The carry over chunks is the affine recurrence h' = decay * h + local, one
-// independent chain per (batch, direction, channel, state) = only B*4*Dm*16 chains: a thread per chain walks ~512
-// chunks with dependent loads on a quarter of the chip.  Here a 1024-thread block covers 64 chains x SEG = 16 segments
-// of the chunk range: every thread composes the affine map of its segment (h -> P h + Q), the 16 maps are combined
-// through LDS, and the segment is walked a second time from its true incoming state.  Lanes run along the chains, so
-// every access is a contiguous 256-byte row segment.
-constexpr int CARRY_SEG = 16;
-__global__ __launch_bounds__(64 * CARRY_SEG) void scan_carry_kernel(float* __restrict__ hstate, const float* __restrict__ decay,
-                                                                    int nchunk, int per) {
-  __shared__ float Ps[CARRY_SEG][64], Qs[CARRY_SEG][64];
-  const int lane = threadIdx.x & 63, seg = threadIdx.x >> 6;
-  const int i = blockIdx.x * 64 + lane, g = blockIdx.y;
-  const bool live = i < per;
-  const int ii = live ? i : per - 1;
-  const int cps = (nchunk + CARRY_SEG - 1) / CARRY_SEG;
-  const int c0 = seg * cps, c1 = min(nchunk, c0 + cps);
-  const size_t base = (size_t)g * nchunk * per + ii;
-  float P = 1.f, Q = 0.f;
-  constexpr int U = 8;  // loads of U chunks are issued together (they do not depend on the recurrence)
-  for (int cc = c0; cc < c1; cc += U) {
-    float hl[U], dc[U];
-#pragma unroll
-    for (int j = 0; j < U; ++j) {
-      const size_t o = base + (size_t)min(cc + j, nchunk - 1) * per;
-      hl[j] = hstate[o];
-      dc[j] = decay[o];
-    }
-#pragma unroll
-    for (int j = 0; j < U; ++j)
-      if (cc + j < c1) {
-        P *= dc[j];
-        Q = fmaf(dc[j], Q, hl[j]);
-      }
-  }
-  Ps[seg][lane] = P;
-  Qs[seg][lane] = Q;
-  __syncthreads();
-  float hin = 0.f;
-  for (int sgm = 0; sgm < seg; ++sgm) hin = fmaf(Ps[sgm][lane], hin, Qs[sgm][lane]);
-  for (int cc = c0; cc < c1; cc += U) {
-    float hl[U], dc[U];
-#pragma unroll
-    for (int j = 0; j < U; ++j) {
-      const size_t o = base + (size_t)min(cc + j, nchunk - 1) * per;
-      hl[j] = hstate[o];
-      dc[j] = decay[o];
-    }
-#pragma unroll
-    for (int j = 0; j < U; ++j)
-      if (cc + j < c1) {
-        if (live) hstate[base + (size_t)(cc + j) * per] = hin;
-        hin = fmaf(dc[j], hin, hl[j]);
-      }
-  }
-}
-
 
 // y = LayerNorm_Dm(y0 + y1 + y2 + y3) * silu(z)        (SS2D.forward, mambair_arch.py:380-384)
 __global__ __launch_bounds__(256) void mamba_norm_gate_kernel(const float* __restrict__ y, size_t ystride, int ldy,

@@ -945,6 +945,84 @@ def selective_scan4(u, xdbl, dtw, dtb, A, Dv, B, H, W, Dm, R, chunk=None):
     return y
 
 
+SCAN_SEQ_D_STATES = (16, 8)     # the d_state values ffsr_selective_scan_f32 is instantiated for
+
+
+def selective_scan_fn(u, delta, A, B, C, D=None, z=None, delta_bias=None, delta_softplus=False,
+                      return_last_state=False, *, chunk=None):
+    """Drop-in for mamba_ssm's ``selective_scan_fn`` (forward only): MambaIR's SS2D binds it as
+    ``self.selective_scan = selective_scan_fn`` (mambair_arch.py:276) and calls it at :356-362.
+
+    u, delta, z [B, Dm, L]; A [Dm, N] (real); B, C [B, G, N, L] or [B, N, L] (G = 1), G dividing Dm; D, delta_bias [Dm];
+    fp32 CUDA tensors, N in SCAN_SEQ_D_STATES.  Returns y [B, Dm, L], or (y, last_state [B, Dm, N]).  Runs on torch's
+    current stream; `chunk` (a multiple of 8) overrides the scan's chunk length.
+
+    Tensors whose last dimension is not unit-stride are made contiguous (as mamba_ssm does); strided views such as the
+    reference's Bs / Cs slices of the x_dbl split are passed as they are.  This is an inference seam: there is no backward
+    pass, so a call under grad mode with an input that requires grad raises instead of returning a result autograd cannot
+    differentiate.  Refusals: TypeError (non-CUDA or non-fp32 tensors), NotImplementedError (complex A, non-variable 2-D
+    B / C, unsupported N, autograd), ValueError (inconsistent shapes), hip.FfsrError (arguments the library rejects, e.g. G
+    not dividing Dm).  There is no torch fallback."""
+    named = dict(u=u, delta=delta, A=A, B=B, C=C, D=D, z=z, delta_bias=delta_bias)
+    given = {k: t for k, t in named.items() if t is not None}
+    for k, t in given.items():
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"selective_scan_fn: {k} must be a tensor")
+        if t.is_complex():
+            raise NotImplementedError(f"selective_scan_fn: complex {k} is not supported")
+    if B.dim() == 2 or C.dim() == 2:
+        raise NotImplementedError("selective_scan_fn: non-variable (2-D) B / C are not supported")
+    for k, t in given.items():
+        if not t.is_cuda:
+            raise TypeError(f"selective_scan_fn: {k} is on {t.device}; the HIP scan needs GPU tensors")
+        if t.dtype != torch.float32:
+            raise TypeError(f"selective_scan_fn: {k} is {t.dtype}; only float32 is supported")
+    if len({t.device for t in given.values()}) != 1:
+        raise TypeError("selective_scan_fn: all tensors must be on one device")
+    if torch.is_grad_enabled() and any(t.requires_grad for t in given.values()):
+        raise NotImplementedError("selective_scan_fn is forward-only (no backward pass): call it under torch.no_grad() "
+                                  "or with inputs that do not require grad")
+    if u.dim() != 3:
+        raise ValueError(f"selective_scan_fn: u must be [B, Dm, L], got {tuple(u.shape)}")
+    Bsz, Dm, L = u.shape
+    if A.dim() != 2 or A.shape[0] != Dm:
+        raise ValueError(f"selective_scan_fn: A must be [Dm={Dm}, N], got {tuple(A.shape)}")
+    N = A.shape[1]
+    if N not in SCAN_SEQ_D_STATES:
+        raise NotImplementedError(f"selective_scan_fn: d_state N = {N} is not instantiated (have {SCAN_SEQ_D_STATES})")
+    B = B.unsqueeze(1) if B.dim() == 3 else B
+    C = C.unsqueeze(1) if C.dim() == 3 else C
+    G = B.shape[1]
+    for k, t, shape in (("delta", delta, (Bsz, Dm, L)), ("z", z, (Bsz, Dm, L)), ("B", B, (Bsz, G, N, L)),
+                        ("C", C, (Bsz, G, N, L)), ("D", D, (Dm,)), ("delta_bias", delta_bias, (Dm,))):
+        if t is not None and tuple(t.shape) != shape:
+            raise ValueError(f"selective_scan_fn: {k} must be {list(shape)}, got {list(t.shape)}")
+
+    def unit_last(t):
+        return t if t is None or t.stride(-1) == 1 else t.contiguous()
+
+    u, delta, z = unit_last(u), unit_last(delta), unit_last(z)
+    # the kernel reads B and C with one set of strides and a state row stride of L (the x_dbl views satisfy both);
+    # any other layout gets the contiguous copy mamba_ssm would make
+    if B.stride() != C.stride() or B.stride()[2:] != (L, 1):
+        B, C = B.contiguous(), C.contiguous()
+    A, D, delta_bias = (None if t is None else t.contiguous() for t in (A, D, delta_bias))
+
+    chunk = chunk or scan_chunk(L, Bsz * G * -(-(Dm // G) // 64))     # waves per chunk: (batch, group, 64 channels)
+    nchunk = -(-L // chunk)
+    dev = u.device
+    y = torch.empty(Bsz, Dm, L, device=dev)
+    last = torch.empty(Bsz, Dm, N, device=dev) if return_last_state else None
+    hstate = torch.empty(Bsz, nchunk, Dm, N, device=dev)
+    decay = torch.empty_like(hstate)
+    sz = (0, 0) if z is None else (z.stride(0), z.stride(1))
+    hip.call("ffsr_selective_scan_f32", _ptr(u), _ptr(delta), _ptr(A), _ptr(B), _ptr(C), _ptr(D), _ptr(z),
+             _ptr(delta_bias), _ptr(y), _ptr(last), _ptr(hstate), _ptr(decay), u.stride(0), u.stride(1),
+             delta.stride(0), delta.stride(1), sz[0], sz[1], B.stride(0), B.stride(1), Bsz, Dm, L, N, G,
+             int(bool(delta_softplus)), chunk, _stream())
+    return (y, last) if return_last_state else y
+
+
 def mamba_norm_gate(y4, z, gamma, beta, eps=1e-5, out=None, out_planes=None, want_f32=True):
     """y4 [4, M, C], z [M, C] (row stride ldz) -> LayerNorm(sum_k y4[k]) * silu(z); out_planes as in layernorm()."""
     nd, M, C = y4.shape

@@ -283,6 +283,20 @@ int ffsr_pixel_mha_f32(const float* qkv, int ldq, float* out, int ldo, long long
 int ffsr_selective_scan4_f32(const float* u, int ldu, const float* xdbl, int ldx, const float* dtw, const float* dtb,
                              const float* A, const float* Dv, float* y, int ldy, float* hstate, float* decay, int B,
                              int H, int W, int Dm, int R, int d_state, int chunk, void* stream);
+/* mamba_ssm's selective_scan_fn (forward) on its own layouts: the one native seam of the reference, bound there as
+ * `self.selective_scan = selective_scan_fn` (mambair_arch.py:276) and called at mambair_arch.py:356-362.
+ *   delta = softplus?(delta + delta_bias);  h_t = exp(delta_t A[d]) h_{t-1} + delta_t B[b, g(d), :, t] u[b, d, t]
+ *   y_t = <C[b, g(d), :, t], h_t> + D[d] u[b, d, t];  y *= silu(z) if z;  last_state[b, d, :] = h_{L-1} if requested.
+ * u, delta, z [B, Dm, L] with (batch, channel) strides su_*, sdt_*, sz_* (in floats); y [B, Dm, L] contiguous;
+ * A [Dm, N] contiguous; Bm, Cm [B, G, N, L] with batch / group strides sbc_b, sbc_g and state stride L (the reference's
+ * Bs / Cs are such views of the x_dbl split: sbc_g = (R + 2N) L); channel d is in group d / (Dm / G); D, delta_bias [Dm];
+ * last_state [B, Dm, N] contiguous.  Every last dimension is unit-stride.  D, z, delta_bias, last_state may be NULL.
+ * N = 16 or 8, G divides Dm, L > 0, chunk % 8 == 0; hstate / decay: scratch [B, ceil(L / chunk), Dm, N] each. */
+int ffsr_selective_scan_f32(const float* u, const float* delta, const float* A, const float* Bm, const float* Cm,
+                            const float* D, const float* z, const float* delta_bias, float* y, float* last_state,
+                            float* hstate, float* decay, long long su_b, long long su_d, long long sdt_b, long long sdt_d,
+                            long long sz_b, long long sz_d, long long sbc_b, long long sbc_g, int Bsz, int Dm, int L,
+                            int N, int G, int softplus, int chunk, void* stream);
 /* out = LayerNorm(y0 + y1 + y2 + y3) * silu(z): mambair_arch.py:380-384.  ystride = elements between directions. */
 int ffsr_mamba_norm_gate_f32(const float* y, long long ystride, int ldy, const float* z, int ldz, const float* gamma,
                              const float* beta, float eps, float* out, int ldo, int M, int C, void* stream);
